@@ -369,6 +369,35 @@ def solve_mode(args, tcn, fzn, rank, world, local_rank, dist, tdev, capi, tdist,
     return 0
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_STATS = ("nodes", "fails", "solutions", "num_deductions", "best_bound")
+
+
+def search_outputs(has: bool, best, st: dict) -> dict:
+    """What one search launch hands its caller (session.finish(): has_solution, best store, stats) as named arrays: the best store's
+    bounds and the search's counters (not its timers)."""
+    import numpy as np
+    out = {"has_solution": np.array([int(has)]), "best_lb": best["lb"], "best_ub": best["ub"]}
+    out.update({f"stats_{k}": np.array([st[k]]) for k in DUMP_STATS})
+    return out
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: every array as <out_dir>/<name>.npy in float64 (exact for the engine's int32 bounds and its counters), at most
+    DUMP_LIMIT_BYTES in all.  An array above its share of that is replaced by a sample at fixed, seeded positions (the same in every run,
+    for every array of that length), and the positions are written beside it as <name>_index.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64).ravel()
+        if a.nbytes > share:
+            keep = np.sort(np.random.default_rng(0).choice(a.size, share // 16, replace=False))
+            np.save(os.path.join(out_dir, f"{name}_index.npy"), keep.astype(np.float64))
+            a = a[keep]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def launch_ranks(n: int) -> int:
     """`python bench.py --gpus N` on its own: run the N ranks as FRESH child processes (one per GPU, torch.distributed.run on
     127.0.0.1) and relay what they print.  This process never imports torch and never touches a GPU; it exits with the
@@ -430,7 +459,11 @@ def main() -> int:
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--dist-backend", default=None, choices=["nccl", "gloo"], help="default nccl (= RCCL); gloo with --share-device (RCCL refuses two ranks on one GPU)")
     ap.add_argument("--share-device", action="store_true", help="testing aid: every rank uses cuda:0")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy in float64 (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.dist_backend is None:
         args.dist_backend = "gloo" if args.share_device else "nccl"
 
@@ -509,17 +542,17 @@ def main() -> int:
             sess = capi.Session(tcn, cfg)
         return sess, linked
 
-    def one_step(sess, linked: bool) -> dict:
+    def one_step(sess, linked: bool):
+        """One search launch; returns what session.finish() hands the caller: (has_solution, best store, stats)."""
         if world == 1 or linked:
-            _, _, st = tdist.run_linked(sess, dist if world > 1 else None)
-            return st
+            return tdist.run_linked(sess, dist if world > 1 else None)
         sess.arm()
         dist.barrier()
         sess.start()
         tdist.exchange_until_done(sess, dist, tensor_device=tdev, period_s=0.0002)
-        _, _, st = sess.finish()
+        out = sess.finish()
         dist.barrier()
-        return st
+        return out
 
     def sync():
         if world > 1:
@@ -535,9 +568,10 @@ def main() -> int:
                 "num_blocks_done", "cumulative_time_block_ns", "eps_solved_subproblems", "eps_skipped_subproblems", "active_lane_evaluations")
         tot = {k: 0 for k in keys}
         tot["start_times"] = []
-        last = None
+        last = result = None
         for _ in range(steps):
-            last = one_step(sess, linked)
+            result = one_step(sess, linked)
+            last = result[2]
             for k in keys:
                 tot[k] += last[k]
             tot["start_times"].append(last.get("host_start_time", 0.0))
@@ -559,7 +593,7 @@ def main() -> int:
             dist.all_reduce(hi, op=dist.ReduceOp.MAX)
             dist.all_reduce(lo, op=dist.ReduceOp.MIN)
             g["start_skew_ms_max"] = float((hi - lo).max().item()) * 1000.0
-        return elapsed, tot, g, last
+        return elapsed, tot, g, last, result
 
     if args.mode == "solve":
         rc = solve_mode(args, tcn, fzn, rank, world, local_rank, dist, tdev, capi, tdist, torch)
@@ -572,8 +606,10 @@ def main() -> int:
     budget = (args.nodes_total or (budget_event if args.fixpoint == "event" else budget_sweep)) * scale
     session, linked = make_session(args.fixpoint, budget)
     plan = session.plan()
-    elapsed, tot, glob, last = timed(session, linked, args.steps, args.warmup)
-    steps = max(args.steps, 1)
+    elapsed, tot, glob, last, last_result = timed(session, linked, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, search_outputs(*last_result))
+    steps = args.steps
 
     # per-rank balance: kernel time, share of workgroup-time spent without a subproblem, stolen work
     blocks = max(1, last["num_blocks"])
@@ -598,7 +634,7 @@ def main() -> int:
             b2 = args.nodes_total or (budget_event if other == "event" else (budget_sweep if other == "wac1" else max(1, budget_sweep // 6)))
             b2 *= scale
             sess2, linked2 = make_session(other, b2)
-            e2, _, g2, l2 = timed(sess2, linked2, args.side_steps, 1)
+            e2, _, g2, l2, _ = timed(sess2, linked2, args.side_steps, 1)
             sides.append({"fixpoint": other, "steps": args.side_steps, "nodes_total": b2, "nodes_per_sec": g2["nodes"] / e2,
                           "propagations_per_sec": g2["num_deductions"] / e2, "ms_per_step": e2 * 1000.0 / args.side_steps,
                           "workgroups_per_gpu": l2["num_blocks"], "threads": l2["threads_per_block"],
@@ -621,7 +657,7 @@ def main() -> int:
                 b2 = WORKLOADS[name][1] if fp == "event" else WORKLOADS[name][2]
                 sess2, _ = make_session(fp, b2, tcn2)
                 pl2 = sess2.plan()
-                e2, t2, g2, l2 = timed(sess2, False, args.other_steps, 1)
+                e2, t2, g2, l2, _ = timed(sess2, False, args.other_steps, 1)
                 ks2 = t2["kernel_ns"] * 1e-9 / args.other_steps
                 roof2 = roofline_record(info0, l2["mem_kind"], t2["num_deductions"] / args.other_steps, t2["store_writes"] / args.other_steps, ks2)
                 attach_counters(roof2, name, fp, ks2)

@@ -266,11 +266,48 @@ def test_bench_refuses_a_world_size_that_contradicts_gpus():
     assert not [l for l in p.stdout.splitlines() if l.startswith("{")]
 
 
+def test_bench_refuses_fewer_than_one_timed_step():
+    """`ms_per_step` divides the timed window by --steps: a run without a timed step has no such number and is refused."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0", "--no-cpu-baseline"], env=_clean_env(),
+                       capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert p.returncode != 0 and "--steps must be at least 1" in p.stderr
+    assert not [l for l in p.stdout.splitlines() if l.startswith("{")]
+
+
+def test_bench_dump_writes_float64_arrays_within_the_limit(tmp_path):
+    """--dump-outputs: the search's results as float64 .npy files; an output above its share of the 64 MB is a sample at seeded positions
+    (the same in every run), with the positions written beside it."""
+    import bench
+    stats = {"nodes": 144_000_123, "fails": 77, "solutions": 3, "num_deductions": 2**40 + 1, "best_bound": -16}
+    for n in (1234, 3_000_000):
+        best = np.zeros(n, dtype=frontend.ITV_DTYPE)
+        best["lb"] = np.arange(n) - 5
+        best["ub"] = np.arange(n) + 2**31 - 1 - n
+        runs = []
+        for rep in range(2):
+            d = tmp_path / f"{n}_{rep}"
+            bench.dump_outputs(str(d), bench.search_outputs(True, best, stats))
+            assert sum(f.stat().st_size for f in d.iterdir()) <= 64 << 20
+            runs.append({f.stem: np.load(f) for f in d.iterdir()})
+        a = runs[0]
+        assert set(a) == set(runs[1]) and all(np.array_equal(a[k], runs[1][k]) for k in a)
+        assert all(x.dtype == np.float64 for x in a.values())
+        assert a["has_solution"][0] == 1 and a["stats_num_deductions"][0] == 2**40 + 1 and a["stats_best_bound"][0] == -16
+        if n == 1234:  # small enough: written whole
+            assert "best_lb_index" not in a
+            idx = np.arange(n)
+        else:
+            assert np.array_equal(a["best_lb_index"], a["best_ub_index"])
+            idx = a["best_lb_index"].astype(np.int64)
+            assert 0 < len(idx) < n and len(np.unique(idx)) == len(idx)
+        assert np.array_equal(a["best_lb"], best["lb"][idx]) and np.array_equal(a["best_ub"], best["ub"][idx])
+
+
 def test_bench_launcher_starts_child_ranks_and_relays_their_failure():
     """`python bench.py --gpus 2` without WORLD_SIZE: the parent spawns two ranks under torch.distributed.run.  Here there is no
     GPU, so every rank stops with the engine's "no CPU fallback" message; the launcher exits non-zero and prints no result line."""
-    import torch
-    if torch.cuda.is_available():
+    # (the engine counts the devices: once it has loaded its HIP runtime into this process, torch's own device query cannot be trusted here)
+    if capi.lib().tb_device_count() > 0:
         pytest.skip("CPU-only check")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--no-cpu-baseline", "--side-steps", "0"],
                        env=_clean_env(), capture_output=True, text=True, timeout=300, cwd=ROOT)
